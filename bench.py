@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the VAME RNN-VAE training hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 `python bench.py --gpus N` without a torchrun environment launches the N ranks itself (re-exec under
@@ -413,6 +413,29 @@ def timed_region(step, steps, world, sync, dev, info=None):
     return dt, terms
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_WHOLE_BYTES = 1 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write each array as out_dir/<name>.npy (float64 stays float64, every other dtype becomes float32), so that two
+    builds run with the same arguments can be compared output for output.  When the arrays hold more than 64 MB in all, every array
+    above 1 MB keeps the same fraction of its rows (first axis), drawn from a fixed seed: the same rows for the same shapes."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    whole = sum(a.nbytes for a in host.values() if a.nbytes <= DUMP_WHOLE_BYTES)
+    large = sum(a.nbytes for a in host.values() if a.nbytes > DUMP_WHOLE_BYTES)
+    frac = 1.0 if whole + large <= DUMP_LIMIT_BYTES else (DUMP_LIMIT_BYTES - whole) / large
+    for name, a in host.items():
+        if frac < 1.0 and a.nbytes > DUMP_WHOLE_BYTES:
+            rows = np.random.default_rng(0).choice(a.shape[0], max(1, int(a.shape[0] * frac)), replace=False)
+            a = a[np.sort(rows)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def release_leg(on_gpu):
     """Between two legs of one bench process: drop everything the finished leg allocated (model, engine workspaces, the ops module's
     scratch caches) and hand the device memory back, so that every leg starts from the allocator state of a fresh process."""
@@ -425,9 +448,11 @@ def release_leg(on_gpu):
         torch.cuda.empty_cache()
 
 
-def train_leg(dev, H, T, B, steps, warmup, rank, world, repeats=1, profile=True, dump=False, one_rank_leg=False, engine_options=None, graph=False):
+def train_leg(dev, H, T, B, steps, warmup, rank, world, repeats=1, profile=True, dump=False, one_rank_leg=False, engine_options=None, graph=False,
+              dump_dir=None):
     """Build the model at (H, T), run `warmup` untimed + `repeats` timed regions of `steps` steps.  Returns a dict with the region
-    times, the last loss terms, the roofline block (GPU only) and -- several ranks -- the collective's own numbers."""
+    times, the last loss terms, the roofline block (GPU only) and -- several ranks -- the collective's own numbers.  `dump_dir`: rank 0
+    writes what the last timed step left to its caller (loss terms, updated weights, their gradients) there (dump_outputs)."""
     from vame_amd.model.dataloader import DeviceWindowLoader
     from vame_amd.model.rnn_model import RNN_VAE
     from vame_amd.model.rnn_vae import FusedAdamAMSGrad, allreduce_gradients
@@ -463,6 +488,9 @@ def train_leg(dev, H, T, B, steps, warmup, rank, world, repeats=1, profile=True,
         dt, terms = timed_region(step, steps, world, sync, dev, info)
         dts.append(dt)
         infos.append(info)
+    if dump_dir is not None and rank == 0:           # before the collective and profiling steps below overwrite the gradients
+        named = list(model.named_parameters())
+        dump_outputs(dump_dir, dict(loss_terms=terms, **{"weight." + k: p for k, p in named}, **{"grad." + k: p.grad for k, p in named}))
     last = [float(v) for v in terms.cpu()]
     assert all(np.isfinite(last)), f"non-finite loss terms {last}"
     res = dict(dts=dts, last=last, mflop=train_mflop_per_window(H, T), roofline=None, distributed=None, mhz=infos[0].get("mhz"),
@@ -521,8 +549,9 @@ def collective_block(model, step, steps, rank, world, sync, dev, dt_n, one_rank_
     return out
 
 
-def embed_leg(dev, n_win_per_rank, rank, world, H=256, T=30, engine_options=None):
-    """Encoder-only latent embedding of a synthetic series, window index range sharded over ranks (no collective on the data path)."""
+def embed_leg(dev, n_win_per_rank, rank, world, H=256, T=30, engine_options=None, dump_dir=None):
+    """Encoder-only latent embedding of a synthetic series, window index range sharded over ranks (no collective on the data path).
+    `dump_dir`: rank 0 writes its shard of the latents there (dump_outputs)."""
     from vame_amd.analysis.pose_segmentation import embed_series
     from vame_amd.model.rnn_model import RNN_VAE
     torch.manual_seed(19)
@@ -553,6 +582,8 @@ def embed_leg(dev, n_win_per_rank, rank, world, H=256, T=30, engine_options=None
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     assert torch.isfinite(out).all()
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, dict(latent=out))
     value = n_win / dt
     # encoder (two bi-GRU layers) + both Lambda heads, matmul flops, 2 / MAC: 96.707 MFLOP per window at H = 256, T = 30
     mflop = (2 * T * 2 * 3 * H * (F + H) + 2 * T * 2 * 3 * H * (2 * H + H) + 2 * 2 * 4 * H * Z) / 1e6
@@ -647,6 +678,9 @@ def main():
     ap.add_argument("--embed-windows", type=int, default=2_000_000)
     ap.add_argument("--hidden", type=int, default=256, help="exploration only (BASELINE config 4 uses 512)")
     ap.add_argument("--time-window", type=int, default=30, help="exploration only (BASELINE config 4 uses 60)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (train: loss terms, updated weights, gradients; embed: "
+                         "the latents) as DIR/<name>.npy, at most 64 MB in all (a fixed-seed sample of rows beyond that)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -670,7 +704,7 @@ def main():
 
     H, T, B = args.hidden, args.time_window, args.batch
     if args.mode == "embed":
-        out = embed_leg(dev, args.embed_windows, rank, world, H, T)
+        out = embed_leg(dev, args.embed_windows, rank, world, H, T, dump_dir=args.dump_outputs)
         if rank == 0:
             out.update(higher_is_better=True, scaling="weak", dtype="f32", data="synthetic")
             if not args.no_cpu_baseline and world == 1 and on_gpu:
@@ -680,7 +714,7 @@ def main():
         headline = (H, T, B) == (256, 30, 4096)
         extras = headline and not args.no_also
         res = train_leg(dev, H, T, B, args.steps, args.warmup, rank, world, repeats=3 if extras else 1,
-                        dump=args.dump_kernels, one_rank_leg=True, graph=args.graph)
+                        dump=args.dump_kernels, one_rank_leg=True, graph=args.graph, dump_dir=args.dump_outputs)
         also = None
         if extras and world == 1 and on_gpu:
             # the other two single-GPU configurations of BASELINE.json under the same clock, each with its own roofline, and the batch

@@ -222,7 +222,8 @@ class VAEEngine:
         self._nuc_event = None            # recorded on the side stream after the solve
         self._drop_mask = None
         self._rng = None                  # device state of the reparameterisation's N(0,1) stream (seed_rng)
-        self.capturing = False            # inside a hipGraph stream capture (rnn_vae.GraphedTrainStep): no event queries, no host copies
+        self.capturing = False            # inside a hipGraph stream capture (rnn_vae.GraphedTrainStep): no event queries, no host copies,
+                                          # no side streams (_may_fork)
         self._eps_used = None
         self.packed_version = -1
         self.version = 0          # bumped by the owner whenever flat_p changes
@@ -415,10 +416,17 @@ class VAEEngine:
         ops.gemm(M, N, K, A, 1, B, 1, self.g, N, c_off=self.table.off(gname) + row_off * N, splitk=sk, ws=ws,
                  a_gap_at=gap_at, a_gap=gap)
 
+    def _may_fork(self):
+        """Whether work may leave the caller's stream for a side stream.  Not on the host emulator, and not while a step is being
+        captured into a graph: a graph whose captured launches branch over several streams crashed the HIP runtime's graph launch
+        (host-side segmentation fault in the first replay, inside its set-up of the streams for the graph's parallel branches), so a
+        captured step stays on one stream.  The results are the same bits either way."""
+        return self.dev.type == "cuda" and not self.capturing
+
     def _parallel(self, jobs, n):
         """Run independent launch closures on up to n streams (round-robin), joined before returning.  Only for groups of
         kernels that are not next to a GRU launch (see _flush_wgrads) and share no scratch."""
-        if self.dev.type != "cuda" or n < 2 or len(jobs) < 2:
+        if not self._may_fork() or n < 2 or len(jobs) < 2:
             for j in jobs:
                 j()
             return
@@ -447,9 +455,9 @@ class VAEEngine:
         jobs, self._wgrad_queue = self._wgrad_queue, None
         if not jobs:
             return
-        n = (self.wgrad_streams or (4 if (self._B_bwd or 0) <= 1024 else 1)) if self.dev.type == "cuda" else 1
+        n = (self.wgrad_streams or (4 if (self._B_bwd or 0) <= 1024 else 1)) if self._may_fork() else 1
         skinny = []
-        if self.skinny_side and n == 1 and self.dev.type == "cuda":
+        if self.skinny_side and n == 1 and self._may_fork():
             # large batches: the narrow contractions (an output dimension <= 32: the layer-0 / decoder dW_ih, the output heads', Lambda's)
             # stream their K = batch x time operand at HBM speed with the matrix pipes nearly idle, the wide ones are MFMA-bound with
             # HBM nearly idle -> the narrow ones run on a side stream beside the wide ones, starting BEHIND the dominant grouped launch
@@ -920,7 +928,7 @@ class VAEEngine:
         z, mu, logvar = self.latent(hn, B, eps, training, want_kl=want_kl)
         eps = self._eps_used
         if cluster is not None:
-            if self.nuc_side and training and self.dev.type == "cuda":
+            if self.nuc_side and training and self._may_fork():
                 self._nuc_pending = (B,) + tuple(cluster)             # issued by decode() right behind the decoders' GRU launch
             else:
                 self.cluster_terms(B, *cluster)
@@ -1062,7 +1070,7 @@ class VAEEngine:
             self.join_cluster()                  # (off by default: see nuc_join_before_coop)
         self._gru_bwd(rows, B)
         ev_dec = None
-        if self.bwd_overlap and self.dev.type == "cuda" and s.future:
+        if self.bwd_overlap and self._may_fork() and s.future:
             ev_dec = torch.cuda.Event()
             ev_dec.record()
         He = H
