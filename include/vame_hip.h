@@ -220,6 +220,31 @@ int vame_nuclear_f32(const float* G, int Z, int kloss, int nrows, float lmbda, f
 int vame_kmeans_assign_f32(const float* X, int64_t N, int D, const float* C, int K, int* labels, float* mind2,
                            float* onehot, int Kp, void* stream);
 
+/* ---- UMAP of the latent vectors (vame/analysis/umap_visualization.py:47-111 runs umap.UMAP(n_components=2, min_dist, n_neighbors,
+ * random_state).fit_transform); the host side is vame_amd/analysis/umap_hip.py.
+ * Exact Euclidean kNN of the N rows of X (N, D): row i of idx / dist (N, k; int32 / f32) holds i itself at distance 0 in slot 0, then
+ * the k - 1 nearest other points by ascending distance, ties to the lower index.  dist is the distance (not its square), accumulated
+ * as sum (x - y)^2 in dimension order.  1 <= D <= 64, 2 <= k <= 256, k <= N, N*k < 2^31. */
+int vame_knn_f32(const float* X, int64_t N, int D, int k, int* idx, float* dist, void* stream);
+/* Smooth-kNN calibration of the kNN rows above: rho[i] = smallest non-zero distance; sigma[i] by a 64-step bisection so that
+ * sum_{s=1..k-1} exp(-max(0, d_is - rho_i) / sigma_i) = log2 k (to 1e-5), floored at 1e-3 x the row's mean distance (rho > 0) or
+ * 1e-3 x mean_dist (the mean over all rows, rho = 0); w (N, k) = 0 where idx == i, 1 where d <= rho or sigma = 0, else
+ * exp(-(d - rho) / sigma). */
+int vame_umap_membership_f32(const float* dist, const int* idx, int64_t N, int k, double mean_dist, float* rho, float* sigma, float* w,
+                             void* stream);
+/* Fuzzy union of the kNN graph's two directions: p[i,s] = w_ij + w_ji - w_ij w_ji for j = idx[i,s] (w_ji = 0 if i is not among j's
+ * neighbours; p = 0 where j == i); rev[i,s] = 1 if i is among j's neighbours.  ws: vame_umap_union_ws_bytes(N, k) bytes of scratch
+ * (the rows sorted by index). */
+int64_t vame_umap_union_ws_bytes(int64_t N, int k);
+int vame_umap_fuzzy_union_f32(const int* idx, const float* w, int64_t N, int k, float* p, int* rev, void* ws, int64_t ws_bytes,
+                              void* stream);
+/* One SGD epoch of the 2-D layout over the symmetric CSR graph (indptr int64 N+1, indices int32, rate = p / max p): yout (N, 2) from
+ * yin (N, 2, the previous epoch; yin != yout).  Edge e is due when floor((epoch+1) rate_e) > floor(epoch rate_e); vertex i then takes
+ * two clipped attractive steps towards its neighbour and 5 negative samples drawn by Philox4x32-10 (counter (e, epoch, draw / 4),
+ * key seed), learning rate alpha, curve parameters a, b.  Deterministic: the same inputs give the same bits. */
+int vame_umap_epoch_f32(const float* yin, float* yout, int64_t N, const int64_t* indptr, const int* indices, const float* rate, int epoch,
+                        float alpha, float a, float b, uint64_t seed, void* stream);
+
 /* out[b,c] = sum_t in[(b*T+t)*ld + c], c < C (C % 4 == 0): sum over time of a (B,T,ld) sequence -- the
  * gradient wrt the time-constant decoder input z (vame/model/rnn_model.py:169-170). */
 int vame_timesum_f32(const float* in, int B, int T, int C, int64_t ld, float* out, void* stream);

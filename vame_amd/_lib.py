@@ -5,7 +5,7 @@ There is no CPU fallback: every op in :mod:`vame_amd.ops` goes through this C AB
 """
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvame_hip.so")
@@ -53,6 +53,12 @@ _SIGS = {
     "vame_nuclear_state_doubles": (c_int64, [c_int]),
     "vame_nuclear_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vame_kmeans_assign_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "vame_knn_f32": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "vame_umap_membership_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vame_umap_union_ws_bytes": (c_int64, [c_int64, c_int]),
+    "vame_umap_fuzzy_union_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "vame_umap_epoch_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_uint64,
+                                    c_void_p]),
     "vame_timesum_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p]),
     "vame_colsum_ws_floats": (c_int64, [c_int64, c_int]),
     "vame_colsum_f32": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p]),

@@ -8,7 +8,7 @@ unmodified on the MI355X path.  It is opt-in (call it, or install the one-line `
 tools/install_vame_alias.py writes) and it refuses to shadow a reference package that is already imported.
 
 Only what the build implements is aliased (train / embed path and its neighbouring drivers); the reference's other
-entry points (init_new_project, motif_videos, community, umap visualisation, gif, csv_to_numpy, egocentric_alignment --
+entry points (init_new_project, motif_videos, community, gif, csv_to_numpy, egocentric_alignment --
 vame/__init__.py:14,19-28) raise an AttributeError that says so instead of pretending to exist.
 """
 import importlib
@@ -25,11 +25,13 @@ _MODULES = {
     "vame.analysis": "vame_amd.analysis",
     "vame.analysis.pose_segmentation": "vame_amd.analysis.pose_segmentation",
     "vame.analysis.generative_functions": "vame_amd.analysis.generative_functions",
+    "vame.analysis.umap_visualization": "vame_amd.analysis.umap_visualization",
     "vame.util": "vame_amd.util",
     "vame.util.auxiliary": "vame_amd.util.auxiliary",
 }
-_TOP_LEVEL = ("create_trainset", "train_model", "evaluate_model", "pose_segmentation", "generative_model")     # vame/__init__.py:15-18,23
-_NOT_ON_THE_PATH = ("init_new_project", "motif_videos", "community", "community_videos", "visualization", "gif", "csv_to_numpy",
+_TOP_LEVEL = ("create_trainset", "train_model", "evaluate_model", "pose_segmentation", "generative_model",      # vame/__init__.py:15-18,23
+              "visualization")                                                                                  # :22
+_NOT_ON_THE_PATH = ("init_new_project", "motif_videos", "community", "community_videos", "gif", "csv_to_numpy",
                     "egocentric_alignment", "update_config")
 
 

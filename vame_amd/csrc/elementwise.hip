@@ -99,19 +99,9 @@ extern "C" int vame_window_gather_f32(const float* X, int64_t N, int F, const in
 // --------------------------------------------------------------------------------- latent fwd/bwd
 __device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 
-// Counter-based N(0,1) draw for the reparameterisation (rnn_model.py:71-74: `epsilon = torch.randn_like(...)`): Philox4x32-10 keyed by the
-// caller's seed, counter = (element index, step), Box-Muller on two of its four words.  A draw depends on (seed, step, element) only --
-// reproducible, independent of the launch geometry, nothing to carry between launches but the step number.
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&out)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
+// Counter-based N(0,1) draw for the reparameterisation (rnn_model.py:71-74: `epsilon = torch.randn_like(...)`): Philox4x32-10 (vame_device.h)
+// keyed by the caller's seed, counter = (element index, step), Box-Muller on two of its four words.  A draw depends on (seed, step, element)
+// only -- reproducible, independent of the launch geometry, nothing to carry between launches but the step number.
 __device__ __forceinline__ float philox_normal(uint64_t idx, uint64_t seed, uint64_t step) {
     uint32_t r[4];
     philox4x32_10((uint32_t)idx, (uint32_t)(idx >> 32), (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);

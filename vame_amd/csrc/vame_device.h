@@ -148,6 +148,19 @@ __device__ __forceinline__ float fast_sigmoid(float x) { return VAME_RCP(1.0f + 
 // tanh(x) = 1 - 2/(exp(2x)+1): absolute error ~1e-7, saturates correctly for |x| large
 __device__ __forceinline__ float fast_tanh(float x) { return 1.0f - 2.0f * VAME_RCP(VAME_EXPF(2.0f * x) + 1.0f); }
 
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC 2011): counter (c0..c3), key (k0, k1) -> four words.
+// Shared by the reparameterisation draw (elementwise.hip) and the negative sampling of the UMAP layout (umap.hip).
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&out)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);

@@ -522,6 +522,34 @@ def kmeans_assign(X, N, D, C, K, labels, mind2=None, onehot=None, Kp=0):
     _lib.check(rc, "vame_kmeans_assign_f32")
 
 
+def knn(X, N, D, k, idx, dist):
+    """Exact Euclidean kNN of the rows of X (N, D): idx (N, k) int32 / dist (N, k), slot 0 = the point itself."""
+    assert idx.dtype == torch.int32
+    rc = _lib.lib().vame_knn_f32(_ptr(X), N, D, k, _ptr(idx), _ptr(dist), _stream())
+    _lib.check(rc, "vame_knn_f32")
+
+
+def umap_membership(dist, idx, N, k, mean_dist, rho, sigma, w):
+    rc = _lib.lib().vame_umap_membership_f32(_ptr(dist), _ptr(idx), N, k, float(mean_dist), _ptr(rho), _ptr(sigma), _ptr(w), _stream())
+    _lib.check(rc, "vame_umap_membership_f32")
+
+
+def umap_fuzzy_union(idx, w, N, k, p, rev):
+    """p (N, k) = the fuzzy union weight of each kNN entry, rev (N, k) int32 = 1 where the entry is also in the other row."""
+    assert idx.dtype == torch.int32 and rev.dtype == torch.int32
+    nbytes = int(_lib.lib().vame_umap_union_ws_bytes(N, k))
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=idx.device)
+    rc = _lib.lib().vame_umap_fuzzy_union_f32(_ptr(idx), _ptr(w), N, k, _ptr(p), _ptr(rev), _ptr(ws), nbytes, _stream())
+    _lib.check(rc, "vame_umap_fuzzy_union_f32")
+
+
+def umap_epoch(yin, yout, N, indptr, indices, rate, epoch, alpha, a, b, seed):
+    assert indptr.dtype == torch.int64 and indices.dtype == torch.int32
+    rc = _lib.lib().vame_umap_epoch_f32(_ptr(yin), _ptr(yout), N, _ptr(indptr), _ptr(indices), _ptr(rate), int(epoch), float(alpha),
+                                        float(a), float(b), int(seed) & 0xffffffffffffffff, _stream())
+    _lib.check(rc, "vame_umap_epoch_f32")
+
+
 def timesum(inp, B, T, C, ld, out):
     rc = _lib.lib().vame_timesum_f32(_ptr(inp), B, T, C, ld, _ptr(out), _stream())
     _lib.check(rc, "vame_timesum_f32")
